@@ -114,6 +114,32 @@ def launch_ranks(n: int) -> int:
     return 0
 
 
+DUMP_SAMPLE = 1 << 20                                                # elements kept of each large flat buffer (4 MB as float32)
+
+
+def dump_outputs(out_dir, eng, last):
+    """What a step handed back (loss, student / teacher feature std) and left in the engine (updated student and teacher
+    parameters, the head BatchNorm buffers), as DIR/<name>.npy.  The flat buffers hold tens of millions of
+    values: a fixed sample of DUMP_SAMPLE of them (sorted indices of a seeded draw, the same for every run at the same arguments)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    loss, std_s, std_t = last
+    arrays = {"loss": np.asarray([float(loss)], np.float64), "std_student": np.asarray([float(std_s)], np.float64),
+              "std_teacher": np.asarray([float(std_t)], np.float64)}
+    for name, buf in (("student_params", eng.p32), ("teacher_params", eng.t32)):
+        n = buf.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.RandomState(0).choice(n, DUMP_SAMPLE, replace=False))
+            arrays[name] = buf[torch.from_numpy(idx).to(buf.device)].float().cpu().numpy()
+        else:
+            arrays[name] = buf.float().cpu().numpy()
+    for key, bufs in eng.bn_buffers.items():
+        for b, t in bufs.items():
+            arrays[f"bn.{key}.{b}"] = t.detach().cpu().numpy().astype(np.float64 if t.dtype in (torch.float64, torch.int64) else np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def build_job(workload, arch, dtype, hires, B, world, rank, dev, total, precise=False, overlap=False):
     """Engine + resident synthetic input + the step closure of one workload (the headline, or one of the `also` passes).
     One step = mel front end of every view -> teacher fwd -> student fwd -> loss -> student bwd -> (all-reduce) -> fused HF-AdamW + EMA."""
@@ -165,11 +191,11 @@ def build_job(workload, arch, dtype, hires, B, world, rank, dev, total, precise=
             if ncrops == 6:                                  # 4 local views of 1 s -> 101 frames -> 25 patches + CLS
                 mels += [fe(buf[:, o[2 + v]:o[2 + v] + clip_len // 10], out=l_buf[v * B:(v + 1) * B]) for v in range(4)]
                 lens += [torch.full((B,), Tl)] * 4
-        loss, _, _ = eng.forward(mels, lens, masks)
+        loss, std_s, std_t = eng.forward(mels, lens, masks)
         eng.backward()
         eng.allreduce_grads()
         eng.optimizer_step(float(lr_tab[k]), float(wd_tab[k]), float(ema_tab[k + 1]))
-        return loss
+        return loss, std_s, std_t
 
     return eng, step, dict(frame=frame, ncrops=ncrops, patch=patch, khz="32kHz" if hires else "16kHz")
 
@@ -209,6 +235,11 @@ def main():
                     help="HIP events around one launch in n of each kernel kind, a hashed subset of the launch indices (1 = all: costs ~6 %% of the step; 7: ~0.6 %%; "
                          "17: ~0.3 %% -- events fence the overlap of consecutive kernels and of the two streams)")
     ap.add_argument("--overlap", action="store_true", help="run the teacher pass on a second HIP stream")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, replay the last timed step's batch on a freshly built engine (same seeds: a reproducible "
+                         "state) and write what the step computed to DIR/<name>.npy (float32 / float64, < 64 MB: loss, feature stds, "
+                         "BatchNorm buffers in full; updated student and teacher parameters as a fixed seeded sample) -- "
+                         "same arguments, same inputs: two builds compare output for output")
     ap.add_argument("--backend", default=os.environ.get("ATST_DIST_BACKEND", "nccl"), choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (one rank per GPU); gloo = test transport, lets several ranks share one GPU")
     args = ap.parse_args()
@@ -264,9 +295,10 @@ def main():
         lib.atst_profile_enable(args.profile_stride)
     t0 = time.perf_counter()
     for k in range(args.warmup, args.warmup + args.steps):
-        loss = step(k)
+        last = step(k)
     sync()
     dt = time.perf_counter() - t0
+    loss = last[0]
     lib.atst_profile_enable(0)
     if os.environ.get("ATST_BENCH_MEM"):        # soak runs: allocator state after the timed region (stderr; not part of the JSON contract)
         print(f"[bench] rank {rank}: max allocated {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB, reserved {torch.cuda.memory_reserved() / 2**30:.2f} GiB",
@@ -440,6 +472,28 @@ def main():
             torch.cuda.empty_cache()
             if os.environ.get("ATST_BENCH_MEM"):
                 print(f"[bench] after `also` {wl} {arch} {dtype}: allocated {torch.cuda.memory_allocated() / 2**30:.2f} GiB, reserved {torch.cuda.memory_reserved() / 2**30:.2f} GiB", file=sys.stderr)
+
+    if args.dump_outputs:
+        # The state a timed step starts from is not the same from run to run: the backward's fp32 atomics (weight-gradient splits,
+        # bias / LayerNorm column sums) leave summation-order noise in every gradient (~6e-4 rel after one backward, amplified by the
+        # BatchNorm backward), and AdamW turns a sign flip of a near-zero gradient entry into a full learning-rate step -- after 25 steps
+        # two identical runs are 3 % apart.  The dump therefore comes from a fresh engine built exactly as the headline's (same seeds,
+        # same arguments), through the same step function, on the batch and schedule values of the last timed step: its forward is
+        # bit-identical from run to run, and the AdamW update normalises the gradient noise away.
+        import gc
+        eng = step = None
+        gc.collect()
+        torch.cuda.empty_cache()
+        torch.manual_seed(4321 + rank)
+        k_last = args.warmup + args.steps - 1
+        eng, step, _ = build_job(args.workload, args.arch, args.dtype, args.hires, B, world, rank, dev, total, args.precise, args.overlap)
+        last = step(k_last)
+        sync()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, eng, last)
+        eng = step = None
+        gc.collect()
+        torch.cuda.empty_cache()
 
     # N ranks on N distinct devices, as RCCL sees them: every rank reports its device index and PCI bus id
     rccl = None

@@ -15,16 +15,43 @@ def _free_port():
 
 
 def _worker(rank, world, port, q):
+    """One rank per process."""
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
+    _rank(rank, world, q)
+
+
+def _threaded_ranks(world, q):
+    """Every rank of the world as a thread of ONE process, each with its own gloo process group (thread-local c10d state, a
+    shared in-process store).  A process that imports torch loads the GPU runtime: eight rank processes next to a test
+    session that holds the GPU would be more GPU processes than a shared GPU node allows."""
+    import threading
+    from torch.testing._internal.distributed.multi_threaded_pg import ThreadLocalWorld
+    c10d = dist.distributed_c10d
+    c10d._world = ThreadLocalWorld()
+    c10d._register_process_group = lambda name, pg: None    # by-name registry is process-wide: every rank's default group is "0"
+    store = dist.HashStore()
+
+    def run(rank):
+        dist.init_process_group("gloo", store=store, rank=rank, world_size=world)
+        _rank(rank, world, q)
+
+    threads = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+
+
+def _rank(rank, world, q):
     from audiossl_amd import parallel as P
-    torch.manual_seed(0)
+    gen = torch.Generator().manual_seed(0)                                      # per rank: threaded ranks share the global generator
     N = 64
     cuts = [0, 9, 22] if world == 2 else [0, 3, 9, 10, 17, 22, 30, 33, 41]     # ragged shards (ATST-Frame: masked-row counts differ per rank)
     R = cuts[-1]
-    h = torch.randn(R, N, dtype=torch.float64) * 2 + 0.5
-    gamma, beta = torch.rand(N, dtype=torch.float64) + 0.5, torch.randn(N, dtype=torch.float64) * 0.1
-    w_out = torch.randn(N, dtype=torch.float64)
+    h = torch.randn(R, N, dtype=torch.float64, generator=gen) * 2 + 0.5
+    gamma, beta = torch.rand(N, dtype=torch.float64, generator=gen) + 0.5, torch.randn(N, dtype=torch.float64, generator=gen) * 0.1
+    w_out = torch.randn(N, dtype=torch.float64, generator=gen)
     lo, hi = cuts[rank], cuts[rank + 1]
     hl = h[lo:hi]
     # ---- forward statistics
@@ -44,7 +71,8 @@ def _worker(rank, world, port, q):
     ok = ok and torch.allclose(dh, hr.grad[lo:hi]) and torch.allclose(s1, br.grad) and torch.allclose(s2, gr.grad)
     # ---- DDP gradient mean: local-mean-loss gradients summed then scaled by 1/world == global-mean-loss gradient
     #      (equal shard sizes, as drop_last + DistributedSampler give)
-    X = torch.randn(16, 5, dtype=torch.float64); t = torch.randn(16, dtype=torch.float64); w = torch.randn(5, dtype=torch.float64)
+    X = torch.randn(16, 5, dtype=torch.float64, generator=gen); t = torch.randn(16, dtype=torch.float64, generator=gen)
+    w = torch.randn(5, dtype=torch.float64, generator=gen)
     idx = list(P.shard(16, rank, world))
     g_local = (2 * (X[idx] @ w - t[idx])[:, None] * X[idx]).mean(0)
     flat = g_local.clone()
@@ -52,7 +80,7 @@ def _worker(rank, world, port, q):
     g_full = (2 * (X @ w - t)[:, None] * X).mean(0)
     ok = ok and summed and torch.allclose(flat / world, g_full)
     # ---- two independent BatchNorms in ONE exchange (teacher + student projector of a step): same numbers as one by one
-    h2 = torch.randn(R, N, dtype=torch.float64) * 0.7 - 1.0
+    h2 = torch.randn(R, N, dtype=torch.float64, generator=gen) * 0.7 - 1.0
     h2l = h2[lo:hi]
     m_b = h2l.mean(0); q_b = ((h2l - m_b) ** 2).sum(0)
     (ma, qa, ca), (mb, qb, cb) = P.combine_bn_stats_multi([(mean_l, m2_l, hl.shape[0]), (m_b, q_b, h2l.shape[0])])
@@ -71,10 +99,13 @@ def _worker(rank, world, port, q):
 def test_sharded_ranks_equal_one_rank(world):
     ctx = mp.get_context("spawn")
     q, port = ctx.Queue(), _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    if world <= 2:
+        procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    else:                                                                       # world 8: one process, eight rank threads
+        procs = [ctx.Process(target=_threaded_ranks, args=(world, q))]
     for p in procs:
         p.start()
-    res = sorted(q.get(timeout=240) for _ in procs)
+    res = sorted(q.get(timeout=240) for _ in range(world))
     for p in procs:
         p.join(timeout=60)
     assert res == [(r, True) for r in range(world)]

@@ -84,11 +84,15 @@ def test_two_ranks_equal_one_rank_on_the_concatenated_batch(tmp_path, mode, over
 
 @pytest.mark.parametrize("mode", ["clip", "frame"])
 def test_eight_ranks_equal_one_rank_on_the_concatenated_batch(tmp_path, mode):
-    """configs[3] readiness on the single-GPU box (BASELINE.json: 8 x MI355X DDP): EIGHT ranks (gloo, all on cuda:0 unless the node has
-    8 GPUs), 4 clips each, against one process on the 32-clip batch.  Exercises what world 2 cannot: the bucket cuts with seven
-    peers, the SyncBN combine of eight [mean, M2, count] rows, rank -> device mapping, eight DIFFERENT initial seeds aligned by the one
-    init broadcast.  Tolerances: the 4-clips-per-rank regime of the two-rank test (BatchNorm-backward cancellation amplifies the fp32
-    summation-order difference more with fewer rows per rank)."""
+    """configs[3] (BASELINE.json: 8 x MI355X DDP): EIGHT ranks, one per GPU (RCCL), 4 clips each, against one process on the 32-clip
+    batch.  Exercises what world 2 cannot: the bucket cuts with seven peers, the SyncBN combine of eight [mean, M2, count] rows,
+    rank -> device mapping, eight DIFFERENT initial seeds aligned by the one init broadcast.  Tolerances: the 4-clips-per-rank regime
+    of the two-rank test (BatchNorm-backward cancellation amplifies the fp32 summation-order difference more with fewer rows per rank).
+    Needs 8 GPUs: eight ranks sharing fewer devices would keep more processes on one GPU than a shared node allows."""
+    import torch
+    ndev = torch.cuda.device_count()
+    if ndev < 8:
+        pytest.skip(f"needs 8 GPUs, found {ndev}")
     one = _worker(tmp_path, f"one8_{mode}", 1, mode, batch=4, ranks=8)
     eight = _worker(tmp_path, f"eight_{mode}", 8, mode, 1, batch=4, ranks=8)
     assert int(eight["world"]) == 8 and float(eight["same"][0]) == 1.0      # all ranks hold identical parameters after the step
