@@ -95,6 +95,24 @@ int atst_gemm_nt_lnbwd_q8(const void* dY, const void* Wt, int operands_fp8, int 
   a.q8 = g8; a.q8_scale_ptr = g8_scale; a.q8_amax = g8_amax;
   return atst_gemm_nt(a, ST(stream));
 }
+// the side outputs of the fused epilogues as engine.hip sets them (gemm8 / gemm8_bwd / the bf16 dGELU of the recording step), for the kernel-level tests
+int atst_gemm_nt_q8(const void* A, const void* B, int operands_fp8, int M, int N, int K, int lda, int ldb, int epi, void* C, int ldc, void* C2,
+                    const float* bias, const float* resid, const float* row_scale, int rows_per_seq, const uint16_t* U, float* colsum,
+                    const float* dq, float dq_mul, const atst_gemm_q8_t* x, void* stream) {
+  const atst_gemm_q8_t z{};
+  const atst_gemm_q8_t& q = x ? *x : z;
+  if (!A || !B || epi == EPI_PATCH || epi == EPI_LNBWD || (epi == EPI_RESID && !resid) || (epi == EPI_DGELU && !U)) return ATST_EINVAL;
+  if (!operands_fp8 && (q.resid_bf16 || q.out_bf16 || q.a_scale_dev)) return ATST_EINVAL;     // the bf16 residual stream exists on e4m3 operands only
+  if ((q.resid_bf16 || q.out_bf16) && epi != EPI_RESID) return ATST_EINVAL;
+  GemmArgs a{};
+  a.A = reinterpret_cast<const bf16*>(A); a.B = reinterpret_cast<const bf16*>(B); a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.epi = epi;
+  a.C = C; a.ldc = ldc; a.C2 = C2; a.bias = bias; a.resid = resid; a.row_scale = row_scale; a.rows_per_seq = rows_per_seq > 0 ? rows_per_seq : 1;
+  a.U = CBF(U); a.colsum = colsum;
+  if (operands_fp8) { a.fp8 = 1; a.dq = dq; a.dq_mul = dq_mul; a.dq_div = q.a_scale_dev; }
+  a.q8 = q.q8; a.q8_scale = q.q8_scale; a.q8_scale_ptr = q.q8_scale_dev; a.q8_amax = q.q8_amax; a.q8_sat = q.q8_sat;
+  a.resid_bf16 = q.resid_bf16; a.out_bf16 = q.out_bf16;
+  return atst_gemm_nt(a, ST(stream));
+}
 int atst_quant_fp8_bf16(const uint16_t* x, size_t n, float scale, uint8_t* y, void* stream) { return atst_quant_fp8(CBF(x), n, scale, y, ST(stream)); }
 int atst_quant_fp8_dyn_bf16(const uint16_t* x, size_t n, const float* scale, uint8_t* y, float* amax, void* stream) {
   return atst_quant_fp8_dyn(CBF(x), n, scale, y, amax, ST(stream));
@@ -155,6 +173,22 @@ int atst_layernorm_bwd(const uint16_t* dy, const float* x, const float* mean, co
   a.dy = CBF(dy); a.x = x; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.dres = dres; a.dx = dx; a.g = BF(g);
   a.row_scale = row_scale; a.rows_per_seq = rows_per_seq > 0 ? rows_per_seq : 1; a.dgamma = dgamma; a.dbeta = dbeta;
   a.dbias_up = dbias_up; a.M = M; a.C = C;
+  return atst_ln_bwd(a, ST(stream));
+}
+int atst_layernorm_fwd_q8(const void* x, int x_is_bf16, const float* gamma, const float* beta, uint16_t* y, float* mean, float* rstd, int M, int C,
+                          uint8_t* y8, float s8, const float* s8_dev, float* amax_site, uint32_t* sat, void* stream) {
+  if (!x || !gamma || !beta || !y8 || !mean || !rstd) return ATST_EINVAL;
+  if (x_is_bf16) return atst_ln_fwd_b16in(CBF(x), gamma, beta, BF(y), mean, rstd, M, C, ST(stream), y8, s8, sat, s8_dev, amax_site);
+  return atst_ln_fwd(static_cast<const float*>(x), gamma, beta, BF(y), mean, rstd, M, C, ST(stream), y8, s8, sat, s8_dev, amax_site);
+}
+int atst_layernorm_bwd_q8(const uint16_t* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                          const float* dres, float* dx, uint16_t* g, const float* row_scale, int rows_per_seq,
+                          float* dgamma, float* dbeta, float* dbias_up, int M, int C, uint8_t* g8, const float* g8_scale, float* g_amax, void* stream) {
+  if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || (g8 && !g8_scale)) return ATST_EINVAL;
+  LnBwdArgs a{};
+  a.dy = CBF(dy); a.x = x; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.dres = dres; a.dx = dx; a.g = BF(g);
+  a.row_scale = row_scale; a.rows_per_seq = rows_per_seq > 0 ? rows_per_seq : 1; a.dgamma = dgamma; a.dbeta = dbeta;
+  a.dbias_up = dbias_up; a.M = M; a.C = C; a.g8 = g8; a.g8_scale = g8_scale; a.g_amax = g_amax;
   return atst_ln_bwd(a, ST(stream));
 }
 

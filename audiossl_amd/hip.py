@@ -33,6 +33,12 @@ class Wgrad8(C.Structure):
                 ("ldw", C.c_int), ("scale_y", C.c_void_p), ("scale_x", C.c_void_p)]
 
 
+class GemmQ8(C.Structure):
+    """atst_gemm_q8_t (include/atst_hip.h): side outputs of atst_gemm_nt_q8"""
+    _fields_ = [("q8", C.c_void_p), ("q8_scale", C.c_float), ("q8_scale_dev", C.c_void_p), ("q8_amax", C.c_void_p), ("q8_sat", C.c_void_p),
+                ("a_scale_dev", C.c_void_p), ("resid_bf16", C.c_int), ("out_bf16", C.c_int)]
+
+
 class Wgrad(C.Structure):
     """atst_wgrad_t (include/atst_hip.h)."""
     _fields_ = [("dY", C.c_void_p), ("X", C.c_void_p), ("dW", C.c_void_p)] + [(n, C.c_int) for n in ("M", "N", "K", "ldy", "ldx", "ldw")]
@@ -73,6 +79,8 @@ _SIGS = {
     "atst_gemm_nt_lnbwd_q8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13 + [C.c_int] + [C.c_void_p] * 4),
     "atst_gemm_nt_fp8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p,
                                    C.c_float, C.c_void_p]),
+    "atst_gemm_nt_q8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 +
+                        [C.c_float, C.c_void_p, C.c_void_p]),
     "atst_quant_fp8_bf16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
     "atst_quant_fp8_dyn_bf16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "atst_fp8_update_scales": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
@@ -86,6 +94,8 @@ _SIGS = {
     "atst_layernorm_fwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
     "atst_layernorm_fwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
     "atst_layernorm_bwd": (C.c_int, [C.c_void_p] * 9 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p]),
+    "atst_layernorm_fwd_q8": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_float] + [C.c_void_p] * 4),
+    "atst_layernorm_bwd_q8": (C.c_int, [C.c_void_p] * 9 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 4),
     "atst_attention_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
     "atst_attention_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p]),
     "atst_attention_fp8_ok": (C.c_int, [C.c_int, C.c_int, C.c_int]),

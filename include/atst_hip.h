@@ -42,7 +42,9 @@ enum { ATST_EPI_BF16 = 0, ATST_EPI_F32 = 1, ATST_EPI_BIAS_GELU = 2, ATST_EPI_RES
  *   120  round 5: atst_encoder_t grew fp8_wgrad / f8_act_scale_bwd ; an fp8 training workspace also holds per-layer e4m3 activation copies
  *        and an e4m3 dqkv ; fp8_lean ; atst_gemm_tn_fp8, atst_gemm_tn_group_fp8, atst_attention_fwd_fp8, atst_attention_bwd_fp8
  *        (round 6 ADDED entry points without changing an existing one -- atst_gemm_nt_resid_ln_fp8, atst_gemm_nt_lnbwd_q8, atst_attention_fp8_ok -- and widened two
- *        preconditions: atst_gemm_tn_fp8 takes N, K multiples of 128, the fp8 attention entries take NP = 32: the version stays 120)                        */
+ *        preconditions: atst_gemm_tn_fp8 takes N, K multiples of 128, the fp8 attention entries take NP = 32: the version stays 120)
+ *        (round 7 ADDED the test entry points atst_gemm_nt_q8 (+ atst_gemm_q8_t), atst_layernorm_fwd_q8, atst_layernorm_bwd_q8 without changing an existing
+ *        one: the version stays 120)                                                                                                                      */
 #define ATST_ABI_VERSION 120
 int atst_version(void);   /* = ATST_ABI_VERSION of the header the library was built from */
 /* Tuning hooks for A/B measurements (tools/gemm_bench.py, env ATST_TUNE=a,b,... read by audiossl_amd/hip.py); defaults are the
@@ -129,6 +131,23 @@ int atst_gemm_nt_lnbwd_q8(const void* dY, const void* Wt, int operands_fp8, int 
 int atst_gemm_nt_fp8(const uint8_t* A8, const uint8_t* B8, int M, int N, int K, int lda, int ldb, int epi, void* C, int ldc,
                      void* C2, const float* bias, const float* resid, const float* row_scale, int rows_per_seq,
                      const float* dq, float dq_mul, void* stream);
+/* Test entry point (round 7): the GEMM with the side outputs its fused epilogues write in the e4m3 step, set the way the encoder sets them -- the
+ * forward e4m3 GEMMs (fc1 + GELU with its e4m3 activation copy, the residual GEMMs of the bf16 residual stream), the e4m3 dGELU dgrad and the bf16 dGELU
+ * of the recording step.  A / B are e4m3 bytes (operands_fp8 = 1: C = epilogue(acc * dq_mul * *dq / *a_scale_dev)) or bf16 (operands_fp8 = 0: dq, dq_mul,
+ * a_scale_dev unused).  x (or NULL = all fields zero):
+ *   q8 / q8_scale / q8_scale_dev: EPI_BIAS_GELU: e4m3(bf16(gelu) * s) [M, ldc], s = *q8_scale_dev or q8_scale ; EPI_DGELU: e4m3(bf16(du) * *q8_scale_dev)
+ *     (or 1).  C (DGELU) / C2 (BIAS_GELU) may be NULL when q8 is given (the lean passes) ;
+ *   q8_amax: an ATST_AMAX_SITE_STRIDE-float site receiving max |gelu| (BIAS_GELU, with q8) or max |du| (DGELU, with or without q8; bf16 operands too) ;
+ *   q8_sat: BIAS_GELU: number of elements of q8 clipped at +-448, added ;
+ *   a_scale_dev: the device scale the accumulators are divided by (delayed scaling of A ; e4m3 operands only) ;
+ *   resid_bf16 / out_bf16: EPI_RESID on e4m3 operands: resid / C are bf16 [M, ldc] instead of fp32 (fp8 inference and teacher passes).
+ * The shapes and epilogues the GEMM launcher accepts are unchanged (ATST_EINVAL otherwise); EPI_PATCH / EPI_LNBWD have entry points of their own.      */
+typedef struct {
+  uint8_t* q8; float q8_scale; const float* q8_scale_dev; float* q8_amax; uint32_t* q8_sat; const float* a_scale_dev; int resid_bf16, out_bf16;
+} atst_gemm_q8_t;
+int atst_gemm_nt_q8(const void* A, const void* B, int operands_fp8, int M, int N, int K, int lda, int ldb, int epi, void* C, int ldc, void* C2,
+                    const float* bias, const float* resid, const float* row_scale, int rows_per_seq, const uint16_t* U, float* colsum,
+                    const float* dq, float dq_mul, const atst_gemm_q8_t* x, void* stream);
 /* y = e4m3(clamp(scale * x, +-448)) for a bf16 tensor of n elements (n % 8 == 0)                                           */
 int atst_quant_fp8_bf16(const uint16_t* x, size_t n, float scale, uint8_t* y, void* stream);
 /* per-tensor-scaled e4m3 shadows of n tensors of a flat fp32 buffer: table int32 [n][2] = {element offset, numel};
@@ -164,6 +183,15 @@ int atst_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta
 int atst_layernorm_bwd(const uint16_t* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                        const float* dres, float* dx, uint16_t* g, const float* row_scale, int rows_per_seq,
                        float* dgamma, float* dbeta, float* dbias_up, int M, int C, void* stream);
+/* Test entry points (round 7): the same LayerNorms with the e4m3 side outputs of the fp8 step.
+ *   atst_layernorm_fwd_q8: x fp32 or bf16 (x_is_bf16: the bf16 residual stream of an fp8 inference pass) ; y (bf16, or NULL) ; y8 = e4m3(bf16(y) * s),
+ *     s = *s8_dev or s8 ; amax_site (or NULL): max |bf16(y)| ; sat (or NULL): elements of y8 clipped at +-448, added.
+ *   atst_layernorm_bwd_q8: atst_layernorm_bwd with g (bf16) nullable, g8 = e4m3(bf16(row_scale dx) * *g8_scale) (or NULL), g_amax (or NULL): max |row_scale dx|. */
+int atst_layernorm_fwd_q8(const void* x, int x_is_bf16, const float* gamma, const float* beta, uint16_t* y, float* mean, float* rstd, int M, int C,
+                          uint8_t* y8, float s8, const float* s8_dev, float* amax_site, uint32_t* sat, void* stream);
+int atst_layernorm_bwd_q8(const uint16_t* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                          const float* dres, float* dx, uint16_t* g, const float* row_scale, int rows_per_seq,
+                          float* dgamma, float* dbeta, float* dbias_up, int M, int C, uint8_t* g8, const float* g8_scale, float* g_amax, void* stream);
 /* Attention.forward + get_attention_mask: audiossl/modules/transformer.py:107-121,152-159                            */
 int atst_attention_fwd(const uint16_t* qkv, const int* valid, uint16_t* o, float* lse, int S, int H, int NP, void* stream);
 /* 1 when the attention kernels of tile size NP write the e4m3 copy themselves (forward: atst_attention_fwd_fp8's o8 ; backward: atst_attention_bwd_fp8's dqkv8):

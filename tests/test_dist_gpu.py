@@ -132,7 +132,7 @@ def test_two_ranks_equal_one_rank_base_fp8(tmp_path, mode):
     # (a site's amax is ONE element: the summation-order difference between the runs moves it by what the e4m3 staircase of its inputs allows -- measured
     # per site: base <= 8.9e-3 (a du site) ; small 6.8e-3 with the LayerNorms as separate passes and 2.0e-2 with them inside the GEMM epilogues, both at
     # block 0's dqkv site, which the attention backward posts; a missing MAX-reduce shows as ranks holding different parameters -- `same` above)
-    assert sg < 4e-2 and sa < 1e-2
+    assert sg < (1e-2 if mode == "base_fp8" else 4e-2) and sa < 1e-2
     assert abs(float(two["loss"][0]) - float(one["loss"][0])) < 2e-3
     assert g < 4e-2, g                                                     # measured 2.1e-2 (loss 3e-6 apart, forward scales identical, gradient scales 1.5e-3 apart)
     assert _rel(two["teacher"], one["teacher"]) < 1e-4

@@ -1089,7 +1089,38 @@ def test_fp8_inference_pass_bf16_residual_stream(arch):
         with torch.no_grad(), O.emulate_bf16(), O.emulate_fp8(resid_bf16=False):
             cls_f = O.encoder_forward(W, "teacher.encoder.", mel, length, arch, depth=depth, drop_path_rate=0.0)
         print(f"[fp8 inference, small, fused LayerNorm epilogues] CLS vs emulation {relerr(feats['shipped'], cls_f):.3e}; vs the separate-pass fp32-stream run {relerr(feats['shipped'], feats[2100]):.3e}")
-        assert relerr(feats["shipped"], cls_f) < 5.5e-2 and relerr(feats["shipped"], feats[2100]) < 6e-2
+        assert relerr(feats["shipped"], cls_f) < 5.5e-2
+        assert relerr(feats["shipped"], feats[2100]) < 1e-3                # measured 0 on these CLS rows: the two LayerNorm forms differ in a few
+                                                                           # elements by one bf16 step (next test), none of them feeds CLS at depth 3
+
+
+def test_fp8_inference_small_fused_layernorm_epilogues_vs_separate_passes():
+    """The shipped d = 384 fp8 inference pass (LayerNorms inside the residual GEMM epilogues, fp32 stream) against the separate-pass fp32-stream run
+    (hooks 2110 + 2100), over EVERY token.  They are not bit-identical: the fused LayerNorm and ln_fwd_kernel reduce the row statistics in different
+    orders, so a LayerNorm output next to a bf16 rounding boundary lands on the other side now and then -- measured at depth 1: 7 of 589,824 elements,
+    each one bf16 step.  Through the e4m3 staircase that grows with depth: measured 4.1e-3 at depth 6, 1.7e-2 at depth 12 (24 residual adds)."""
+    from audiossl_amd.engine import AtstEngine
+    lib = hip.load()
+    S = 6
+    for depth, bound in ((1, None), (12, 2.5e-2)):
+        W = O.recipe_weights("small", depth=depth, seed=95)
+        eng = AtstEngine("small", depth=depth, fp8=True)
+        eng.load_weights(W)
+        mel = O.recipe_mel(S, 1001, seed=97).cuda()
+        valid = eng._valid(torch.tensor([1001, 640, 1001, 1001, 333, 999]), 1)
+        try:
+            shipped = eng._pass("teacher", S, 1001, False, 0).forward(mel, valid, None, None).float().clone()
+            lib.atst_tune_gemm_variant(2110); lib.atst_tune_gemm_variant(2100)
+            separate = eng._pass("teacher", S, 1001, False, 0).forward(mel, valid, None, None).float().clone()
+        finally:
+            lib.atst_tune_gemm_variant(2101); lib.atst_tune_gemm_variant(2111)
+        assert torch.isfinite(shipped).all()
+        if bound is None:                                                  # one LayerNorm pair: a few elements, one bf16 step each
+            d = shipped != separate
+            step = (shipped - separate).abs() / separate.abs().clamp_min(1e-30)
+            assert int(d.sum()) <= 1e-4 * d.numel() and float(step.max()) <= 2.0 ** -7, (int(d.sum()), float(step.max()))
+        else:
+            assert relerr(shipped, separate) < bound, relerr(shipped, separate)
 
 
 def test_fp8_forward_saturation_counter_and_running_scales():
