@@ -225,6 +225,27 @@ int atst_attention_bwd_fp8(const uint16_t* qkv, const int* valid, const uint16_t
   return atst_attn_bwd(a, ST(stream));
 }
 
+// test entry points: AttnArgs filled the way engine.hip does, including the packed row stride
+int atst_attention_fwd_rs(const uint16_t* qkv, const int* valid, uint16_t* o, uint8_t* o8, const float* o8_scale, float* o8_amax, uint32_t* o8_sat,
+                          float* lse, int S, int H, int NP, int stride, void* stream) {
+  if (o8 && !o8_scale) return ATST_EINVAL;
+  AttnArgs a{};
+  a.qkv = CBF(qkv); a.valid = valid; a.o = BF(o); a.lse = lse; a.S = S; a.H = H; a.NP = NP; a.stride = stride;
+  if (o8) { a.o8 = o8; a.o8_scale = o8_scale; a.o8_amax = o8_amax; a.o8_sat = o8_sat; }
+  return atst_attn_fwd(a, ST(stream));
+}
+
+int atst_attention_bwd_rs(const uint16_t* qkv, const int* valid, const uint16_t* o, const float* lse, const uint16_t* d_o,
+                          uint16_t* dqkv, uint8_t* dqkv8, const float* q8_scale, float* q8_amax, float* dscratch,
+                          int S, int H, int NP, int stride, void* stream) {
+  if (!dqkv == !dqkv8) return ATST_EINVAL;                          // exactly one of the two outputs
+  AttnArgs a{};
+  a.qkv = CBF(qkv); a.valid = valid; a.o = BF(const_cast<uint16_t*>(o)); a.lse = const_cast<float*>(lse);
+  a.d_o = CBF(d_o); a.dqkv = BF(dqkv); a.dscratch = dscratch; a.S = S; a.H = H; a.NP = NP; a.stride = stride;
+  if (dqkv8) { a.dqkv8 = dqkv8; a.q8_scale = q8_scale; a.q8_amax = q8_amax; }
+  return atst_attn_bwd(a, ST(stream));
+}
+
 int atst_patchify_bf16(const float* mel, int S, int width, int NP, int use_cls, uint16_t* out, void* stream) {
   return atst_patchify(mel, S, width, NP, use_cls, BF(out), ST(stream));
 }

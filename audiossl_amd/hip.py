@@ -101,6 +101,8 @@ _SIGS = {
     "atst_attention_fp8_ok": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "atst_attention_fwd_fp8": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 3 + [C.c_void_p]),
     "atst_attention_bwd_fp8": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 3 + [C.c_void_p]),
+    "atst_attention_fwd_rs": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_void_p]),
+    "atst_attention_bwd_rs": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 4 + [C.c_void_p]),
     "atst_patchify_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "atst_gather_rows_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "atst_scatter_rows_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

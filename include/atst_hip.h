@@ -44,7 +44,8 @@ enum { ATST_EPI_BF16 = 0, ATST_EPI_F32 = 1, ATST_EPI_BIAS_GELU = 2, ATST_EPI_RES
  *        (round 6 ADDED entry points without changing an existing one -- atst_gemm_nt_resid_ln_fp8, atst_gemm_nt_lnbwd_q8, atst_attention_fp8_ok -- and widened two
  *        preconditions: atst_gemm_tn_fp8 takes N, K multiples of 128, the fp8 attention entries take NP = 32: the version stays 120)
  *        (round 7 ADDED the test entry points atst_gemm_nt_q8 (+ atst_gemm_q8_t), atst_layernorm_fwd_q8, atst_layernorm_bwd_q8 without changing an existing
- *        one: the version stays 120)                                                                                                                      */
+ *        one: the version stays 120)
+ *        (round 7 also ADDED the test entry points atst_attention_fwd_rs, atst_attention_bwd_rs without changing an existing one: the version stays 120) */
 #define ATST_ABI_VERSION 120
 int atst_version(void);   /* = ATST_ABI_VERSION of the header the library was built from */
 /* Tuning hooks for A/B measurements (tools/gemm_bench.py, env ATST_TUNE=a,b,... read by audiossl_amd/hip.py); defaults are the
@@ -210,6 +211,15 @@ int atst_attention_bwd(const uint16_t* qkv, const int* valid, const uint16_t* o,
  * the fp8 training step (atst_encoder_t.fp8_wgrad == 2); ATST_EINVAL for NP = 64 / 128.                                                        */
 int atst_attention_bwd_fp8(const uint16_t* qkv, const int* valid, const uint16_t* o, const float* lse, const uint16_t* d_o,
                            uint8_t* dqkv8, const float* scale, float* amax_site, float* dscratch, int S, int H, int NP, void* stream);
+/* Test entry points (round 7): the same kernels with the row stride between sequences the encoder uses (0 = NP ; stride < NP: PACKED sequences,
+ * NP < 256 only -- rows >= stride of a sequence's last 32-row tile belong to the next sequence and are read as zeros, never written).
+ *   atst_attention_fwd_rs: o8 == NULL: atst_attention_fwd ; otherwise atst_attention_fwd_fp8 (o may then be NULL ; o8_scale required).
+ *   atst_attention_bwd_rs: writes dqkv (bf16) OR dqkv8 (e4m3, with q8_scale and q8_amax: atst_attention_bwd_fp8) -- ATST_EINVAL if both or neither. */
+int atst_attention_fwd_rs(const uint16_t* qkv, const int* valid, uint16_t* o, uint8_t* o8, const float* o8_scale, float* o8_amax, uint32_t* o8_sat,
+                          float* lse, int S, int H, int NP, int stride, void* stream);
+int atst_attention_bwd_rs(const uint16_t* qkv, const int* valid, const uint16_t* o, const float* lse, const uint16_t* d_o,
+                          uint16_t* dqkv, uint8_t* dqkv8, const float* q8_scale, float* q8_amax, float* dscratch,
+                          int S, int H, int NP, int stride, void* stream);
 /* PatchEmbed_v2 gather: audiossl/models/atst/audio_transformer.py:56-75 (bit-exact index map, bf16 values)          */
 int atst_patchify_bf16(const float* mel, int S, int width, int NP, int use_cls, uint16_t* out, void* stream);
 int atst_gather_rows_bf16(const uint16_t* src, const int* rows, int R, int C, float* dst, void* stream);
