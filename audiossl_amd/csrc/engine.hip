@@ -325,7 +325,7 @@ extern "C" int atst_encoder_fwd(const atst_encoder_t* e, void* stream) {
 // Backward over blocks [lo, hi) (descending); head: also the final LayerNorm backward (needs hi == depth); tail: also the
 // token stage (needs lo == 0).  At every block boundary the residual gradient is back in dxA and the bf16 operand of the
 // next block's MLP branch is in w.g, so a split needs no state besides the workspace.
-static int encoder_bwd_range(const atst_encoder_t* e, int lo, int hi, bool head, bool tail, void* stream);
+static int encoder_bwd_range(const atst_encoder_t* e, int lo, int hi, bool head, bool tail, void* stream, const atst_tap_t* taps = nullptr);
 
 extern "C" int atst_encoder_bwd(const atst_encoder_t* e, void* stream) {
   if (!check(e)) return ATST_EINVAL;
@@ -343,8 +343,31 @@ extern "C" int atst_encoder_bwd_range(const atst_encoder_t* e, int lo, int hi, v
   return encoder_bwd_range(e, lo, hi, hi == e->depth, lo == 0, stream);
 }
 
-static int encoder_bwd_range(const atst_encoder_t* e, int lo, int hi, bool head, bool tail, void* stream) {
+// ---- fine-tuning taps (finetune.hip): the last n blocks' outputs through the final LayerNorm, pooled or dense -------------------------
+static bool tap_check(const atst_encoder_t* e, const atst_tap_t* t) {
+  return check(e) && t && e->train && !e->fp8 && e->use_cls && t->n >= 1 && t->tap_first >= 0 && t->tap_first + t->n == e->depth && t->plen &&
+         (t->dense || (t->weight && t->ldf >= (t->avgpool ? 2 : 1) * t->n * e->C));
+}
+
+extern "C" int atst_encoder_tap_fwd(const atst_encoder_t* e, const atst_tap_t* t, void* stream) {
+  if (!tap_check(e, t) || !t->feat) return ATST_EINVAL;
+  const Ws w = carve(e->ws, e->S, e->NP, e->C, e->H, e->depth, e->train, e->fp8, patch_k(e));
+  TapFwdArgs a{};
+  for (int j = 0; j < t->n; ++j) a.x[j] = w.x[2 * (t->tap_first + j) + 2];
+  a.gamma = e->p32 + e->off.norm_w; a.beta = e->p32 + e->off.norm_b;
+  a.plen = t->plen; a.weight = t->weight; a.feat = t->feat; a.ldf = t->ldf;
+  a.S = e->S; a.RS = row_stride(e); a.n_tok = e->n_tok; a.n = t->n; a.avgpool = t->avgpool; a.dense = t->dense;
+  return atst_tap_fwd(a, e->C, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int atst_encoder_bwd_taps(const atst_encoder_t* e, const atst_tap_t* t, void* stream) {
+  if (!tap_check(e, t) || !t->dfeat) return ATST_EINVAL;
+  return encoder_bwd_range(e, 0, e->depth, false, true, stream, t);
+}
+
+static int encoder_bwd_range(const atst_encoder_t* e, int lo, int hi, bool head, bool tail, void* stream, const atst_tap_t* taps) {
   if (!check(e) || !e->train || !e->p16t || !e->g32) return ATST_EINVAL;
+  if (taps && (head || e->fp8)) return ATST_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const Ws w = carve(e->ws, e->S, e->NP, e->C, e->H, e->depth, e->train, e->fp8, patch_k(e));
   const int S = e->S, NP = e->NP, C = e->C, RS = row_stride(e), M = S * RS, D = e->depth;
@@ -392,6 +415,17 @@ static int encoder_bwd_range(const atst_encoder_t* e, int lo, int hi, bool head,
   for (int i = hi - 1; i >= lo; --i) {
     const atst_layer_off_t& lo_ = o.layer[i];
     const LayerWs& l = w.L[i];
+    if (taps && i >= taps->tap_first) {
+      // the tap after block i: its LayerNorm backward adds into the residual gradient (writes it at the topmost tap, which replaces the final
+      // LayerNorm head step) and rewrites g = bf16(s2 * cur), the operand of block i's fc2 backward; at every block boundary cur is dxA
+      TapBwdArgs a{};
+      a.x = w.x[2 * i + 2]; a.gamma = p + o.norm_w; a.plen = taps->plen; a.weight = taps->weight; a.dfeat = taps->dfeat;
+      a.cur = cur; a.g = w.g; a.row_scale = dps(i, 1); a.rows_per_seq = RS;
+      a.dgamma = G + o.norm_w; a.dbeta = G + o.norm_b; a.dbias_up = G + lo_.fc2_b;
+      a.M = M; a.S = S; a.RS = RS; a.n_tok = e->n_tok; a.ldf = taps->ldf; a.n = taps->n; a.j = i - taps->tap_first;
+      a.avgpool = taps->avgpool; a.dense = taps->dense; a.accumulate = i != D - 1;
+      RUN(atst_tap_bwd(a, C, st));
+    }
     // ---- MLP branch: x_out = x_mid + s2 * (fc2(gelu(fc1(LN2(x_mid)))) + b2) ; w.g = s2 * d(x_out)
     // The block's four weight gradients are independent of everything downstream: they are launched together after the
     // attention backward (atst_gemm_tn_group), which is why the two residual-branch gradients live in separate buffers.

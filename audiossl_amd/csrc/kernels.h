@@ -79,6 +79,31 @@ struct LnBwdArgs {
 };
 int atst_ln_bwd(const LnBwdArgs& a, hipStream_t st);
 
+// block taps of the fine-tuning path (finetune.hip): final LayerNorm of the fp32 block outputs, pooled (cls | masked mean, chunk-weighted,
+// accumulated) or dense, and its backward into the residual gradient of the encoder backward
+constexpr int TAP_MAX = 24;          // = ATST_MAX_DEPTH
+struct TapFwdArgs {
+  const float* x[TAP_MAX];           // tap j: fp32 [S*RS, C] residual stream after block tap_first + j
+  const float* gamma; const float* beta;
+  const int* plen;                   // [S] reference patch_length (not clipped to the chunk)
+  const float* weight;               // [S] chunk weight (pooled)
+  float* feat;                       // pooled: [S, ldf] accumulated ; dense: [n, S, 1 + n_tok, C] written
+  int ldf, S, RS, n_tok, n, avgpool, dense;
+};
+int atst_tap_fwd(const TapFwdArgs& a, int C, hipStream_t st);
+struct TapBwdArgs {
+  const float* x;                    // [M, C] fp32 tap (block output)
+  const float* gamma;
+  const int* plen; const float* weight;
+  const float* dfeat;                // pooled [S, ldf] or dense [n, S, 1 + n_tok, C] feature gradient
+  float* cur;                        // [M, C] residual gradient: += dx (accumulate) or = dx
+  bf16* g;                           // [M, C] bf16(row_scale * cur)
+  const float* row_scale; int rows_per_seq;
+  float* dgamma; float* dbeta; float* dbias_up;
+  int M, S, RS, n_tok, ldf, n, j, avgpool, dense, accumulate;
+};
+int atst_tap_bwd(const TapBwdArgs& a, int C, hipStream_t st);
+
 // fused attention, head_dim 64, NP (padded tokens / sequence) in {32, 64, 128, 256}
 struct AttnArgs {
   const bf16* qkv;                   // [S*NP, 3*C]

@@ -186,6 +186,9 @@ class EncoderPass:
         e.row_stride = self.RS
         if net == "student":
             e.p32, e.p16, e.p16t, e.g32 = eng.p32.data_ptr(), eng.p16.data_ptr(), eng.p16t.data_ptr(), eng.g32.data_ptr()
+        elif train:                                     # a teacher training pass: fine-tuning through the inference API (EncoderView)
+            eng.teacher_grad_state()
+            e.p32, e.p16, e.p16t, e.g32 = eng.t32.data_ptr(), eng.t16.data_ptr(), eng.t16t.data_ptr(), eng.tg32.data_ptr()
         else:
             e.p32, e.p16, e.p16t, e.g32 = eng.t32.data_ptr(), eng.t16.data_ptr(), None, None
         e.off = eng.enc_off
@@ -624,6 +627,10 @@ class AtstEngine:
         self._cls_rows: Dict[Tuple[int, int], torch.Tensor] = {}
         self._infer_passes: "OrderedDict[Tuple, EncoderPass]" = OrderedDict()
         self._synced_version = (-1, -1)
+        # fine-tuning state of the teacher net (EncoderView's differentiable path): gradient buffer + transposed bf16 shadows of the encoder,
+        # allocated by the first differentiable call (teacher_grad_state)
+        self.tg32: Optional[torch.Tensor] = None
+        self.t16t: Optional[torch.Tensor] = None
         self.heads = {"teacher.projector": HeadPass(self, "teacher", "projector", self.cfg["embed_dim"]),
                       "student.projector": HeadPass(self, "student", "projector", self.cfg["embed_dim"]),
                       "student.predictor": HeadPass(self, "student", "predictor", HEAD_OUT)}
@@ -662,8 +669,34 @@ class AtstEngine:
 
     def param_view(self, net: str, name: str, grad: bool = False) -> torch.Tensor:
         off, shape = self.layout.entries[name]
-        buf = (self.g32 if grad else self.p32) if net == "student" else self.t32
+        if net == "student":
+            buf = self.g32 if grad else self.p32
+        else:
+            buf = self.teacher_grad_state() if grad else self.t32
         return buf[off:off + math.prod(shape)].view(*shape)
+
+    def teacher_grad_state(self) -> torch.Tensor:
+        """The teacher's fp32 gradient buffer (n_teacher), allocated on first use together with the transposed bf16 shadows of its encoder
+        weights (the B operands of the backward's dgrad GEMMs), which sync_shadows() keeps current from then on."""
+        if self.tg32 is None:
+            L = self.layout
+            self.tg32 = torch.zeros(L.n_teacher, device=self.device)
+            self.t16t = torch.zeros(L.n_teacher, dtype=torch.bfloat16, device=self.device)
+            rows, tiles = [], 0
+            for name, (off, shape) in L.entries.items():
+                if name.startswith("encoder.") and len(shape) == 2:
+                    rows.append((off, shape[0], shape[1], tiles))
+                    tiles += -(-shape[0] // 64) * -(-shape[1] // 64)
+            self._ttr_table = torch.tensor(rows, dtype=torch.int32, device=self.device).contiguous()
+            self._ttr_tiles = tiles
+            self.sync_shadows()
+            self._refresh_teacher_transposes()
+        return self.tg32
+
+    def _refresh_teacher_transposes(self):
+        if self.t16t is not None:
+            hip.call("atst_transpose_bf16_batch", hip.ptr(self.t16), hip.ptr(self.t16t), hip.ptr(self._ttr_table),
+                     self._ttr_table.shape[0], self._ttr_tiles, hip.stream())
 
     def load_weights(self, W: Dict[str, torch.Tensor]):
         """state_dict-keyed ('student.encoder...', 'teacher.projector...') fp32 tensors -> flat buffers + BN buffers."""
@@ -721,6 +754,7 @@ class AtstEngine:
         hip.call("atst_cast_bf16", hip.ptr(self.p32), self.p32.numel(), hip.ptr(self.p16), st)
         hip.call("atst_cast_bf16", hip.ptr(self.t32), self.t32.numel(), hip.ptr(self.t16), st)
         self._refresh_transposes()
+        self._refresh_teacher_transposes()
         self._synced_version = (self.p32._version, self.t32._version)
 
     def _refresh_fp8(self):
@@ -1179,6 +1213,8 @@ class AtstEngine:
                  hip.ptr(self.flags), self.layout.n_student, self.layout.n_teacher, lr, wd, betas[0], betas[1], eps, step_size,
                  ema_m if do_ema else 1.0, (1.0 / self.world) if self._grads_summed else 1.0, hip.stream())
         self._refresh_transposes()
+        if do_ema:
+            self._refresh_teacher_transposes()
         self._synced_version = (self.p32._version, self.t32._version)
 
     def ema_update(self, m: float):
@@ -1188,3 +1224,4 @@ class AtstEngine:
                  hip.ptr(self.p16), hip.ptr(self.t16), hip.ptr(self.flags_ema_only), self.layout.n_student, self.layout.n_teacher,
                  0.0, 0.0, 0.9, 0.999, 1e-6, 0.0, m, 1.0, hip.stream())
         self._refresh_fp8()
+        self._refresh_teacher_transposes()

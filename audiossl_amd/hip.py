@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libatst_hip.so")
 if os.environ.get("ATST_LIB_TAG"):          # experiment builds side by side (audiossl_amd/build.py): A/B runs inside one gpurun call
     LIB_PATH = os.path.join(_HERE, "lib", f"libatst_hip_{os.environ['ATST_LIB_TAG']}.so")
 ATST_MAX_DEPTH = 24
-ABI_VERSION = 120                                     # include/atst_hip.h ATST_ABI_VERSION these bindings were written for
+ABI_VERSION = 121                                     # include/atst_hip.h ATST_ABI_VERSION these bindings were written for
 
 EPI_BF16, EPI_F32, EPI_BIAS_GELU, EPI_RESID, EPI_DGELU, EPI_PATCH, EPI_LNBWD = range(7)
 AMAX_SLOTS, AMAX_SLOT_STRIDE = 16, 64                 # include/atst_hip.h ATST_AMAX_*: a running-amax site is 16 slots, 256 B apart
@@ -63,6 +63,12 @@ class Encoder(C.Structure):
                 ("p8t", C.c_void_p), ("g8_scale", C.c_void_p), ("g8_amax", C.c_void_p), ("fp8_bwd", C.c_int), ("row_stride", C.c_int),
                 ("f8_sat", C.c_void_p), ("f8_act_scale", C.c_void_p), ("f8_act_amax", C.c_void_p),
                 ("fp8_wgrad", C.c_int), ("f8_act_scale_bwd", C.c_void_p), ("fp8_lean", C.c_int)]
+
+
+class Tap(C.Structure):
+    """atst_tap_t (include/atst_hip.h): block taps of the fine-tuning path."""
+    _fields_ = [(n, C.c_int) for n in ("n", "tap_first", "avgpool", "dense")] + \
+               [("feat", C.c_void_p), ("dfeat", C.c_void_p), ("ldf", C.c_int), ("plen", C.c_void_p), ("weight", C.c_void_p)]
 
 
 _SIGS = {
@@ -140,6 +146,8 @@ _SIGS = {
     "atst_encoder_dout": (C.c_void_p, [C.POINTER(Encoder)]),
     "atst_encoder_block_out": (C.c_void_p, [C.POINTER(Encoder), C.c_int]),
     "atst_encoder_tokens": (C.c_void_p, [C.POINTER(Encoder)]),
+    "atst_encoder_tap_fwd": (C.c_int, [C.POINTER(Encoder), C.POINTER(Tap), C.c_void_p]),
+    "atst_encoder_bwd_taps": (C.c_int, [C.POINTER(Encoder), C.POINTER(Tap), C.c_void_p]),
     "atst_profile_enable": (C.c_int, [C.c_int]),
     "atst_profile_kinds": (C.c_int, []),
     "atst_profile_name": (C.c_char_p, [C.c_int]),

@@ -6,6 +6,8 @@ audiossl/methods/atstframe/model.py:24-85 (FrameATST).  Parameters are views int
 """
 from __future__ import annotations
 
+import ctypes as C_
+
 import torch
 from torch import nn
 
@@ -76,7 +78,60 @@ class EncoderView(_Node):
         outs = [y[i].view(S, ep.RS, C)[:, :ep.n_tok + ep.use_cls] for i in range(n)]
         return outs, eng.upload(plen), ep.n_tok
 
+    # -- fine-tuning: the differentiable path ------------------------------------------------------------------------
+    # Taken when grad mode is on, the view belongs to the TEACHER net (load_from_checkpoint(...).model.teacher.encoder, AST_small(),
+    # AST_base()) and one of its own parameters requires grad (the harness's unfreeze(), methods/atst/downstream/model.py:18-41).  Every
+    # chunk runs a bf16 training pass of the teacher encoder (DropPath when self.training, the engine's linspace rates); the tap kernels pool
+    # the final-normed outputs of the last n blocks; backward() runs the encoder backward from those taps into the teacher gradient
+    # buffer and binds the parameters' .grad to views of it.  _keep: optional injected DropPath draws, one [depth, 2, S] 0/1 tensor per chunk.
+    _keep = None
+
+    def _differentiable(self):
+        """True on the fine-tuning path.  A Frame encoder stays on the inference path (no graph, as before): the ATST-Frame embedding helpers
+        (methods/atstframe/embedding.py) call a teacher whose parameters require grad with grad mode on; tap_backward_supported() names
+        the missing piece."""
+        eng = self._eng[0]
+        if eng.frame or not torch.is_grad_enabled() or self._netname != "teacher" or not any(p.requires_grad for p in self.parameters()):
+            return False
+        self.tap_backward_supported(raise_=True)
+        return True
+
+    def tap_backward_supported(self, raise_=False):
+        """Whether this encoder can be fine-tuned through the inference API; with raise_, NotImplementedError naming what is missing."""
+        eng, why = self._eng[0], None
+        if eng.frame:
+            why = "fine-tuning a Frame encoder: the tap LayerNorm / pooling backward exists for the clip encoder only (no per-frame tap backward)"
+        elif eng.fp8:
+            why = "fine-tuning an fp8 engine: the tap backward (atst_encoder_bwd_taps) is bf16 only"
+        elif eng.precise:
+            why = "fine-tuning a precise (parity-mode) engine: the fp32 encoder twin has no tap backward"
+        if why and raise_:
+            raise NotImplementedError(why)
+        return why is None
+
+    @staticmethod
+    def _chunk_plan(total, length, chunk_len):
+        """[(start, end, cur_len, chunk_mark)] of get_intermediate_layers_chunks (ref: audio_transformer.py:257-279)."""
+        plan = []
+        for i in range(total // chunk_len + 1):
+            start, end = i * chunk_len, min((i + 1) * chunk_len, total)
+            if end <= start:
+                continue
+            cur = torch.clip(length - i * chunk_len, 0)
+            mark = (cur > 0) if i == 0 else (cur > chunk_len // 2)
+            plan.append((start, end, cur, mark))
+        return plan
+
+    def _tap_apply(self, x, chunks, n, avgpool, dense):
+        """chunks: [(start, end, cur_len or None, weight [S] or None)] -> pooled features [S, (1 + avgpool) n C] or n dense [S, 1 + T, C]."""
+        if not hasattr(self, "_anchor"):
+            self._anchor = torch.zeros((), device=self._eng[0].device, requires_grad=True)
+        out = _TapFn.apply(self._anchor, self, x, chunks, n, avgpool, dense)
+        return list(out) if dense else out[0]
+
     def forward(self, x, mask_index=None, length=None, avg=False):
+        if self._differentiable():
+            return self._tap_apply(x, [(0, x.shape[-1], length, None)], 1, False, False)
         outs, plen, _ = self._blocks(x, length, 1)
         y = outs[0]
         if self.use_cls:
@@ -89,6 +144,8 @@ class EncoderView(_Node):
         Frame encoder: FrameAST.get_intermediate_layers (ref: methods/atstframe/audio_transformer.py:259-281) -- the last n
         norm_frame'd block outputs concatenated on the feature axis, mean-pooled over the valid frames when ``scene``
         ([S, n*C]) or as frame sequences ([S, T, n*C]); consumed by atstframe/embedding.py:75,121."""
+        if self._differentiable():
+            return self._tap_apply(x, [(0, x.shape[-1], length, None)], n, False, True)
         outs, plen, _ = self._blocks(x, length, n)
         if self.use_cls:
             return outs
@@ -101,13 +158,13 @@ class EncoderView(_Node):
         total = x.shape[-1]
         length = torch.as_tensor(length)
         dev = self._eng[0].device
+        plan = self._chunk_plan(total, length, chunk_len)
+        if self._differentiable():
+            marks = torch.stack([m.float().cpu() for _, _, _, m in plan])   # [chunks, S]
+            w = marks / marks.sum(0)                                         # the reference's sum(x * mark) / sum(mark) as one weight per chunk
+            return self._tap_apply(x, [(a, b, cur, w[i]) for i, (a, b, cur, _) in enumerate(plan)], n, avgpool, False)
         cls_c, avg_c, marks = [], [], []
-        for i in range(total // chunk_len + 1):
-            start, end = i * chunk_len, min((i + 1) * chunk_len, total)
-            if end <= start:
-                continue
-            cur = torch.clip(length - i * chunk_len, 0)
-            mark = (cur > 0) if i == 0 else (cur > chunk_len // 2)
+        for start, end, cur, mark in plan:
             outs, plen, _ = self._blocks(x[..., start:end], cur, n)
             off = 1 if self.use_cls else 0
             lm = (torch.arange(outs[0].shape[1] - off, device=outs[0].device)[None, :] < plen[:, None]).unsqueeze(-1)
@@ -119,6 +176,85 @@ class EncoderView(_Node):
         avg = (torch.stack(avg_c) * w).sum(0) / w.sum(0)
         parts = list(cls) + (list(avg) if avgpool else [])
         return torch.cat(parts, dim=-1)
+
+
+class _TapFn(torch.autograd.Function):
+    """Features of the teacher encoder's inference API with a graph: forward = one training EncoderPass per chunk + the tap kernels,
+    backward = the encoder backward from the taps (atst_encoder_bwd_taps), gradients bound as ``param.grad`` views of the teacher
+    gradient buffer (the same scheme as _StepFn / ATST._bind_grads)."""
+
+    @staticmethod
+    def forward(ctx, anchor, view, x, chunks, n, avgpool, dense):
+        from ... import hip
+        eng = view._eng[0]
+        eng.sync_shadows()
+        x = x.detach().to(eng.device, torch.float32)
+        S, C, D, pw = x.shape[0], eng.cfg["embed_dim"], eng.depth, eng.patch_w
+        n = min(n, D)
+        keep = view._keep
+        if keep is not None and len(keep) != len(chunks):
+            raise ValueError(f"EncoderView._keep: one [depth, 2, S] draw per chunk ({len(chunks)}), got {len(keep)}")
+        ldf = (2 if avgpool else 1) * n * C
+        feat = None if dense else torch.zeros(S, ldf, device=eng.device)
+        runs = []
+        gen = object()
+        for ci, (start, end, length, weight) in enumerate(chunks):
+            xc = x[..., start:end].contiguous()
+            width = xc.shape[-1]
+            ep = eng._pass("teacher", S, width, True, ("finetune", ci))
+            l = torch.full((S,), width, dtype=torch.int64) if length is None else torch.as_tensor(length).to(torch.int64)
+            plen = (l - l % pw) // pw                                        # reference patch_length, NOT clipped to the chunk
+            valid = (torch.clamp(plen, max=ep.n_tok) + 1).to(torch.int32)
+            dp = None
+            if view.training and (eng.dpr[-1] > 0 or keep is not None):
+                dp = eng.drop_path_scales(S, None if keep is None else keep[ci])
+            ep.forward(xc, valid, None, dp)
+            t = hip.Tap()
+            t.n, t.tap_first, t.avgpool, t.dense = n, D - n, int(bool(avgpool)), int(bool(dense))
+            plen_d = eng.upload(plen.to(torch.int32))
+            wt_d = eng.upload((torch.ones(S) if weight is None else torch.as_tensor(weight, dtype=torch.float32)).contiguous())
+            keep_alive = (plen_d, wt_d)
+            t.plen, t.weight = plen_d.data_ptr(), wt_d.data_ptr()
+            if dense:
+                feat = torch.empty(n, S, ep.n_tok + 1, C, device=eng.device)
+            t.feat, t.ldf = feat.data_ptr(), ldf
+            hip.check(hip.load().atst_encoder_tap_fwd(C_.byref(ep.e), C_.byref(t), hip.stream()), "atst_encoder_tap_fwd")
+            ep._finetune_gen = gen
+            runs.append((ep, t, keep_alive))
+        ctx.view, ctx.runs, ctx.gen, ctx.dense, ctx.n = view, runs, gen, dense, n
+        return tuple(feat.unbind(0)) if dense else (feat,)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        from ... import hip
+        view, eng = ctx.view, ctx.view._eng[0]
+        for ep, _, _ in ctx.runs:
+            if getattr(ep, "_finetune_gen", None) is not ctx.gen:
+                raise RuntimeError("EncoderView: the activation tape of this call was overwritten by a later differentiable call of the same "
+                                   "geometry; call backward() before the next forward")
+        params = [(nm, p) for nm, p in view.named_parameters() if nm != "mask_embed" and p.requires_grad]
+        buf = eng.teacher_grad_state()
+        cleared = [p.grad is None for _, p in params]
+        if all(cleared):
+            buf.zero_()
+        elif any(cleared):
+            for (nm, p), c in zip(params, cleared):
+                if c:
+                    eng.param_view("teacher", "encoder." + nm, grad=True).zero_()
+        for ep, t, _ in ctx.runs:
+            if ctx.dense:
+                dy = torch.stack([gi if gi is not None else torch.zeros(ep.S, ep.n_tok + 1, eng.cfg["embed_dim"], device=eng.device)
+                                  for gi in grads]).float().contiguous()
+            else:
+                dy = grads[0].float().contiguous()
+            t.dfeat = dy.data_ptr()
+            hip.check(hip.load().atst_encoder_bwd_taps(C_.byref(ep.e), C_.byref(t), hip.stream()), "atst_encoder_bwd_taps")
+            t.dfeat = None
+            ep._finetune_gen = None
+        for (nm, p), c in zip(params, cleared):
+            if c or p.grad.data_ptr() != eng.param_view("teacher", "encoder." + nm, grad=True).data_ptr():
+                p.grad = eng.param_view("teacher", "encoder." + nm, grad=True)
+        return (torch.zeros_like(ctx.view._anchor),) + (None,) * 6
 
 
 class _Net(_Node):

@@ -45,8 +45,9 @@ enum { ATST_EPI_BF16 = 0, ATST_EPI_F32 = 1, ATST_EPI_BIAS_GELU = 2, ATST_EPI_RES
  *        preconditions: atst_gemm_tn_fp8 takes N, K multiples of 128, the fp8 attention entries take NP = 32: the version stays 120)
  *        (round 7 ADDED the test entry points atst_gemm_nt_q8 (+ atst_gemm_q8_t), atst_layernorm_fwd_q8, atst_layernorm_bwd_q8 without changing an existing
  *        one: the version stays 120)
- *        (round 7 also ADDED the test entry points atst_attention_fwd_rs, atst_attention_bwd_rs without changing an existing one: the version stays 120) */
-#define ATST_ABI_VERSION 120
+ *        (round 7 also ADDED the test entry points atst_attention_fwd_rs, atst_attention_bwd_rs without changing an existing one: the version stays 120)
+ *   121  fine-tuning: atst_tap_t, atst_encoder_tap_fwd, atst_encoder_bwd_taps */
+#define ATST_ABI_VERSION 121
 int atst_version(void);   /* = ATST_ABI_VERSION of the header the library was built from */
 /* Tuning hooks for A/B measurements (tools/gemm_bench.py, env ATST_TUNE=a,b,... read by audiossl_amd/hip.py); defaults are the
  * measured best.  These are PROCESS-GLOBAL test knobs (plain ints inside the library, read at launch time, no locking): set them from one
@@ -371,6 +372,31 @@ const float* atst_encoder_hp_block_out(const atst_encoder_t* e, int i);
 /* block-level activation taps for tests: fp32 residual stream after block i (i in [0,depth)), train=1 only */
 const float* atst_encoder_block_out(const atst_encoder_t* e, int i);
 const float* atst_encoder_tokens(const atst_encoder_t* e);
+
+/* ---- fine-tuning: the encoder differentiated through its inference API (clip encoder, bf16 training passes) ------------------
+ * Taps are the last n blocks, tap_first = depth - n.  The final LayerNorm (encoder.norm, eps 1e-6) of the fp32 residual stream after
+ * block tap_first + j (the training tape, atst_encoder_block_out) gives, for sequence s:
+ *   pooled (dense = 0), ref get_intermediate_layers_chunks + get_cls_avg, audio_transformer.py:257-366, ACCUMULATED over the chunks of a call:
+ *     feat[s, j C + c]       += weight[s] LN(x)[s, 0, c]                                                   (cls_j)
+ *     feat[s, (n + j) C + c] += weight[s] sum_{t < min(plen[s], n_tok)} LN(x)[s, 1 + t, c] / (plen[s] + 1e-6)   (avg_j, avgpool != 0)
+ *     feat is [S, ldf], ldf >= (1 + avgpool) n C ; weight[s] = chunk mark / sum of the marks over the chunks ; plen = patch_length of the
+ *     chunk's cur_len, NOT clipped to the chunk's n_tok.  forward() = n 1, avgpool 0, weight 1.
+ *   dense (dense = 1), ref get_intermediate_layers, audio_transformer.py:235-255: feat [n, S, 1 + n_tok, C] = LN(x) rows (written).
+ * dfeat: the gradient of feat in the same layout (backward). */
+typedef struct {
+  int n, tap_first, avgpool, dense;
+  float* feat; const float* dfeat;
+  int ldf;
+  const int32_t* plen;     /* [S] device */
+  const float* weight;     /* [S] device (pooled) */
+} atst_tap_t;
+/* forward of the taps of a TRAINING pass whose atst_encoder_fwd has run (train = 1, fp8 = 0, use_cls = 1) */
+int atst_encoder_tap_fwd(const atst_encoder_t* e, const atst_tap_t* t, void* stream);
+/* the encoder backward with the taps as its gradient sources (instead of atst_encoder_dout): from block depth-1 down, the tap LayerNorm
+ * backward at every tapped boundary adds its input gradient into the fp32 residual gradient (the topmost one writes it), rewrites the bf16
+ * operand of the block's fc2 backward and adds into the fc2 bias and final-norm gradients; then the block's backward; then the token
+ * stage.  Gradients accumulate into g32 (p16t: the pass's transposed bf16 shadows).  bf16 only: ATST_EINVAL for fp8.                  */
+int atst_encoder_bwd_taps(const atst_encoder_t* e, const atst_tap_t* t, void* stream);
 
 /* ---- batched spectrogram augmentations, random draws supplied by the caller --------------------- */
 /* RandomResizeCrop.forward, audiossl/transforms/byol_a.py:33-49: in/out [B,H,W] fp32; params [B][4] = (i, j, h, w) of
